@@ -7,18 +7,27 @@ resident in HBM. value = decoded Mbps (the sum of K over CRC-passin
 second); config carries subframes/s. The CPU baseline is the reference's own srslte_chest_dl_estimate
 + srslte_pdsch_decode (oracle/_ref/ref_front) on the same received grids, FFT excluded.
 
-Further legs on the same JSON line: BASELINE configs[1] (4096 x K=6144 code blocks, 8 half-iterations:
-decoder_c2, with its own roofline and the reference AVX2 decoder as its CPU baseline), the same C3
+A plain run (--gpus / --steps / --warmup only) sets up, warms up, times the steps of this headline and
+prints the result line (metric, value, unit, higher_is_better, dtype, ms_per_step = milliseconds per
+timed step, config). --dump-outputs DIR also writes what the last timed step returned, per TB its return
+code, nof_iterations and decoded bytes, as DIR/<name>.npy (float32); the inputs are seeded, so two builds
+can be compared output for output.
+
+Everything else runs under --full: the headline's per-kernel profiling pass with its roofline and VALU
+roofline, the CPU baselines, the detail file, and the further legs on the same JSON line: BASELINE
+configs[1] (4096 x K=6144 code blocks, 8 half-iterations: decoder_c2, with its own roofline and the
+reference AVX2 decoder as its CPU baseline), the same C3
 subframes with all 8 half-iterations (no early stop), an SNR sweep into the waterfall, the 1536-point
 FFT, TM3 (configs[3] shard), mixed bandwidths (configs[4] shard), the 8-bit decoders, PDCCH / PCFICH,
 the subframe queue and the per-call drop-in.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 For N > 1, one rank per GPU: under torch.distributed.run (WORLD_SIZE must equal N), or started by
 bench.py itself when WORLD_SIZE is unset (N child processes, rank r on GPU r). Each rank decodes its
 own shard of the global job (independent subframes, no data-path collective; results gathered to
-rank 0) -> weak scaling. Rank 0 writes the full record to bench_detail.json and prints ONE compact
-JSON line (<= 6 KB: the contract's keys, roofline, valu_roofline, cpu_baseline, one number per leg).
+rank 0) -> weak scaling. Rank 0 prints ONE compact JSON line (<= 6 KB: the contract's keys and, under
+--full, roofline, valu_roofline, cpu_baseline, one number per leg) and, under --full, writes the full
+record to bench_detail.json.
 """
 import argparse
 import ctypes
@@ -498,7 +507,7 @@ def cb_sizes(table, tbs):
 
 def run_traffic(s, torch, dev, steps, warmup, kind, lanes=2, snr_db=None, dist=None, schedules=None,
                 standard_rate=True, early_stop=True, cpu_sample=0, warm_seconds=0.25, rotate=1, tail=0,
-                tail_prio=True, fe_split=False):
+                tail_prio=True, fe_split=False, lean=False, keep_outputs=False):
     """Coded traffic made on the GPU by the transmit chain (srsgpu_traffic.MixedCells), received
     with CRC early stop (max 8 half-iterations, srsUE's default):
     kind "c5" — BASELINE configs[4] per-GPU shard: 1024 subframes per GPU interleaved over cells of
@@ -525,7 +534,10 @@ def run_traffic(s, torch, dev, steps, warmup, kind, lanes=2, snr_db=None, dist=N
     tail 1 / 2: each lane alternates between two DL-SCH engines whose early-stop tails run on a tail
     stream (srsgpu_dlsch_set_tail_stream; 1: one tail stream shared by the lanes, 2: one per lane), so
     a lane's next batch starts while the last one's straggling code blocks finish; tail_prio: the tail
-    streams are high-priority streams; fe_split: each lane's front end on a stream of its own."""
+    streams are high-priority streams; fe_split: each lane's front end on a stream of its own.
+    lean: only the timed loop and its rates (no per-kernel profiling pass, no schedule A/B, no decoder
+    work count; the result records are built only for a multi-rank gather). keep_outputs: the arrays a
+    caller receives from the last timed step come back as host arrays ("_outputs", tb_outputs)."""
     import srsgpu_shard as sh
     import srsgpu_traffic as tr
     rank = dist.get_rank() if dist else 0
@@ -582,14 +594,17 @@ def run_traffic(s, torch, dev, steps, warmup, kind, lanes=2, snr_db=None, dist=N
     el = time.perf_counter() - t0
     gc.enable()
     host_split = [sum(m.host_s[i] for m in ms) for i in (0, 1)]
-    stages, ktab = stage_profile(s, torch, step, steps, KERNELS)
-    ab = schedule_ab(s, torch, step, steps, schedules)
+    outputs = tb_outputs(ms, nranks) if keep_outputs else None  # of the last timed step
+    stages, ktab = ({}, {}) if lean else stage_profile(s, torch, step, steps, KERNELS)
+    ab = None if lean else schedule_ab(s, torch, step, steps, schedules)
     chk = [m.check() for m in ms]
     # decoder work of the last batch: the half-iterations each code block ran (srsgpu_dlsch_cb_halfits)
     # weighted by its K, for the VALU roofline of the whole decoder (first + early-stop launches)
     # (one block size only: the decoder's block order groups blocks by K, not by TB)
-    halfit_bits = 0
+    halfit_bits = None if lean else 0
     for m in ms:
+        if lean:
+            break
         h = m.dlsch.cb_halfits()
         ks_cb = [k for t in m.tb_list for k in cb_sizes(table, t["tbs"])]
         assert len(ks_cb) == h.size, (len(ks_cb), h.size)
@@ -607,14 +622,17 @@ def run_traffic(s, torch, dev, steps, warmup, kind, lanes=2, snr_db=None, dist=N
     # gather of the results to rank 0 (RCCL grouped send/recv on the GPU box)
     recs = {}
     for m in ms:
+        if lean and not dist:
+            break  # nobody to gather to: the records' size follows from the plan
         ret, noiv, data = m.d_ret.cpu().numpy(), m.d_noi.cpu().numpy(), m.d_data.cpu().numpy()
         for t, r, n in zip(m.tb_list, ret, noiv):
             o = t["data_offset"]
             recs[t["sf"]] = sh.pack_tb_record(r, n, data[o:o + t["tbs"] // 8], m.dlsch.read_cb_crc(m.softbuffer_of(t)),
                                               t["tbs"])
     gdev = dev if (dist and dist.get_backend() == "nccl") else torch.device("cpu")  # gloo: host tensors
-    local = torch.from_numpy(np.concatenate([recs[i] for i in mine])).to(gdev)
     sizes = [sh.tb_record_len(p["tbs"]) for p in sf_plan]
+    local = torch.from_numpy(np.concatenate([recs[i] for i in mine]) if recs
+                             else np.zeros(sum(sizes[i] for i in mine), np.uint8)).to(gdev)
     gather_ms = None
     if dist:
         dist.barrier()
@@ -646,9 +664,44 @@ def run_traffic(s, torch, dev, steps, warmup, kind, lanes=2, snr_db=None, dist=N
         n = min(cpu_sample, c["n"])
         out["_cpu_grids"] = c["grid"][:n * c["gsz"]].cpu().numpy().reshape(n, c["gsz"])
         out["_cpu_sf_idx"] = [int(c["sf_idx"][i]) for i in range(n)]
+    if outputs is not None:
+        out["_outputs"] = outputs
     for m in ms:
         m.close()
     return out
+
+
+DUMP_LIMIT_BYTES = 60 * 2 ** 20  # of float32 values, all ranks together
+
+
+def tb_outputs(ms, nranks=1):
+    """What a caller of the receive path holds after the last step, as float32 host arrays: per TB its
+    return code (0 = acked), nof_iterations and decoded bytes, the TBs in each lane's order, lane after
+    lane. tb_bytes is flat (every TB's tbs / 8 bytes in turn). Over DUMP_LIMIT_BYTES the bytes of a
+    fixed sample of the TBs are kept (seeded; tb_index names them), every TB's return code and
+    iterations stay."""
+    ret = np.concatenate([m.d_ret.cpu().numpy() for m in ms])
+    noi = np.concatenate([m.d_noi.cpu().numpy() for m in ms])
+    rows = []
+    for m in ms:
+        data = m.d_data.cpu().numpy()
+        rows += [data[t["data_offset"]:t["data_offset"] + t["tbs"] // 8] for t in m.tb_list]
+    budget = DUMP_LIMIT_BYTES // max(nranks, 1) // 4 - 3 * len(rows)
+    idx = np.arange(len(rows))
+    if sum(r.size for r in rows) > budget:
+        order = np.random.default_rng(7).permutation(len(rows))
+        fits = np.cumsum([rows[i].size for i in order]) <= budget
+        idx = np.sort(order[:int(fits.sum())])
+    return {"tb_ret": ret.astype(np.float32), "tb_nof_iterations": noi.astype(np.float32),
+            "tb_index": idx.astype(np.float32),
+            "tb_bytes": (np.concatenate([rows[i] for i in idx]) if idx.size else np.zeros(0)).astype(np.float32)}
+
+
+def write_outputs(dirname, outputs, rank, nranks):
+    """--dump-outputs: one <name>.npy per array (<name>_rank<r>.npy when several ranks write)"""
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in outputs.items():
+        np.save(os.path.join(dirname, name + ("" if nranks == 1 else "_rank%d" % rank) + ".npy"), a)
 
 
 def run_tm3_coded(s, torch, dev, steps, warmup, snr_db=30.0, lanes=2, dist=None):
@@ -1219,6 +1272,8 @@ HEADLINE_TAIL = 1  # r06_s7: 0.770 against 0.845 ms per batch (three alternated 
 # decoder early-stop launch schedules (srsgpu_tdec_set_schedule) compared by --ab-headline
 HEADLINE_AB = {"auto": {"es_fused": 2, "es_chunk": 8}, "per_halfit": {"es_fused": 0},
                "fused_c8": {"es_fused": 1, "es_chunk": 8}, "hybrid": {"es_fused": 3, "es_chunk": 8}}
+# the legs of --full after the headline
+ALL_LEGS = "c2,fixed8,cached,c3,tm3,tm3c,coded,sweep,n1536,c5,d8,dropin,dci,pcfich,pdcch,rxq"
 
 
 def decoder_valu_roofline(leg):
@@ -1646,6 +1701,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: its per-kernel profiling pass and rooflines, the CPU baselines, "
+                         "every further leg and the detail file. --legs, --no-pipeline and --ab-headline "
+                         "choose parts of this and imply it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the headline's last timed step returned (per TB: return code, "
+                         "nof_iterations, decoded bytes) as DIR/<name>.npy, float32")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-pipeline", action="store_true", help="headline and configs[1] decoder only")
     ap.add_argument("--coded-snr", type=float, default=None,
@@ -1659,12 +1721,18 @@ def main():
                     help="headline early-stop tails: 0 on the lane's stream, 1 on one high-priority tail stream")
     ap.add_argument("--ab-headline", action="store_true",
                     help="A/B the decoder's early-stop launch schedules on the headline workload")
-    ap.add_argument("--legs", default="c2,fixed8,cached,c3,tm3,tm3c,coded,sweep,n1536,c5,d8,dropin,dci,pcfich,pdcch,rxq",
-                    help="legs after the headline (profiling aid); 'distcheck' alone rehearses the multi-rank "
-                         "partition and gather on the CPU (gloo), without a GPU")
-    ap.add_argument("--detail", default=os.path.join(REPO, "bench_detail.json"),
-                    help="file for the full per-leg record (the last stdout line is the compact summary)")
+    ap.add_argument("--legs", default=None,
+                    help="legs after the headline (profiling aid; with --full every leg: %s); 'distcheck' alone "
+                         "rehearses the multi-rank partition and gather on the CPU (gloo), without a GPU" % ALL_LEGS)
+    ap.add_argument("--detail", default=None,
+                    help="file for the full per-leg record (the last stdout line is the compact summary); "
+                         "with --full bench_detail.json beside this script unless given")
     args = ap.parse_args()
+    full = args.full or args.legs is not None or args.no_pipeline or args.ab_headline
+    if args.legs is None:
+        args.legs = ALL_LEGS if full else "none"
+    if args.detail is None and full:
+        args.detail = os.path.join(REPO, "bench_detail.json")
 
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus > 1:
@@ -1726,15 +1794,21 @@ def main():
     # receiver's grants do (pdsch.c:868-1007 is called with a fresh cfg per subframe): the PDSCH / DL-SCH
     # repeat-call caches never hit, every step pays its per-code-block host work
     head = scale_ranks(run_traffic(s, torch, dev, args.steps, args.warmup, "c3_coded", snr_db=HEADLINE_SNR_DB,
-                                   dist=dist, cpu_sample=64 if (rank == 0 and nranks == 1) else 0, lanes=args.lanes,
+                                   dist=dist, cpu_sample=64 if (full and rank == 0 and nranks == 1) else 0,
+                                   lanes=args.lanes,
                                    warm_seconds=1.0, schedules=HEADLINE_AB if args.ab_headline else None,
-                                   rotate=HEADLINE_DESCRIPTOR_SETS, tail=args.tail, fe_split=bool(args.fe_stream)))
+                                   rotate=HEADLINE_DESCRIPTOR_SETS, tail=args.tail, fe_split=bool(args.fe_stream),
+                                   lean=not full, keep_outputs=bool(args.dump_outputs)))
     cpu_grids, cpu_sf = head.pop("_cpu_grids", None), head.pop("_cpu_sf_idx", None)
+    if args.dump_outputs:
+        write_outputs(args.dump_outputs, head.pop("_outputs"), rank, nranks)
     result = None
     if rank == 0:
-        roof, ktable = pipeline_roofline(head, C3_SF)
-        head["kernel_table"] = ktable
-        valu = decoder_valu_roofline(head)
+        roof = valu = None
+        if full:  # from the profiling pass's per-kernel times
+            roof, ktable = pipeline_roofline(head, C3_SF)
+            head["kernel_table"] = ktable
+            valu = decoder_valu_roofline(head)
         result = {
             "metric": METRIC, "value": head["decoded_mbps"], "unit": "Mbps", "n_gpus": nranks, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": head["ms_per_batch"], "higher_is_better": True, "scaling": "weak",
@@ -1951,9 +2025,10 @@ def main():
     if rank == 0:
         # the full record to the detail file; the last stdout line is the compact summary (the driver
         # keeps only the tail of stdout)
-        with open(args.detail, "w") as f:
-            json.dump(result, f)
-        print(compact_summary(result, os.path.basename(args.detail)), flush=True)
+        if args.detail:
+            with open(args.detail, "w") as f:
+                json.dump(result, f)
+        print(compact_summary(result, os.path.basename(args.detail) if args.detail else None), flush=True)
     if dist:
         dist.destroy_process_group()
 

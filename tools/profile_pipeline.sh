@@ -3,6 +3,7 @@
 set -e
 TAG=${1:-pipe}
 export TMPDIR=/tmp
-mkdir -p gpurun_out/$TAG
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -T -d gpurun_out/$TAG/trace -o kt -- python3 bench.py --steps 4 --warmup 1 --no-cpu-baseline > gpurun_out/$TAG/trace.log 2>&1
-cat gpurun_out/$TAG/trace/kt_kernel_stats.csv
+O=${OUT:-bench_out}/$TAG
+mkdir -p $O
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -T -d $O/trace -o kt -- python3 bench.py --steps 4 --warmup 1 --no-cpu-baseline --full > $O/trace.log 2>&1
+cat $O/trace/kt_kernel_stats.csv

@@ -9,7 +9,7 @@ STEPS=${STEPS:-5}
 export TMPDIR=/tmp
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
-BENCH="python3 bench.py --steps $STEPS --warmup 1 --no-cpu-baseline"
+BENCH="python3 bench.py --steps $STEPS --warmup 1 --no-cpu-baseline --full"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -T -d $OUT/trace -o kt -- $BENCH > $OUT/trace.log 2>&1
 timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -T -d $OUT/pmc_fetch -o pmc -- $BENCH > $OUT/pmc_fetch.log 2>&1
 timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -T -d $OUT/pmc_write -o pmc -- $BENCH > $OUT/pmc_write.log 2>&1

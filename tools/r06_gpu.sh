@@ -23,7 +23,7 @@ if [ "$TESTS" != none ]; then
   tail -1 $O/smoke.log
 fi
 if [ "$MODE" = bench ]; then
-  timeout -k 10 700 python bench.py --detail $O/bench_detail.json > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
+  timeout -k 10 700 python bench.py --full --detail $O/bench_detail.json > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
   echo bench done; wc -c $O/bench.json
 fi
 if [ "$TRACE" = trace ]; then
