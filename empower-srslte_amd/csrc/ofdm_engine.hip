@@ -106,6 +106,19 @@ int srsgpu_ofdm_rx_sf_dev(srsgpu_ofdm_t *q, uint32_t nof_sf, const float *d_in, 
   return 0;
 }
 
+int srsgpu_ofdm_rx_sf_rows_dev(srsgpu_ofdm_t *q, uint32_t nof_sf, const void *const *d_rows, uint32_t format,
+                               float in_scale, float *d_out, size_t out_stride) {
+  if (!q || !d_rows || !d_out || format > SRSGPU_SAMPLES_SC8) return -1;
+  const size_t nsym = q->ext_cp ? 12 : 14;
+  if (out_stride < nsym * 12 * q->nof_prb) return -1;
+  const float scale = q->normalize ? 1.0f / sqrtf((float)q->N) : 1.0f;
+  srsgpu::ProfScope ps("k_ofdm_rx", q->st);
+  HIPCHK(srsgpu::launch_ofdm_rx_rows(d_rows, (int)format, in_scale, (float2 *)d_out, out_stride, (int)nof_sf,
+                                     (int)q->N, (int)(12 * q->nof_prb), q->d_tw, q->radices, q->nstages, scale,
+                                     q->ext_cp, q->st));
+  return 0;
+}
+
 int srsgpu_ofdm_tx_sf_dev(srsgpu_ofdm_t *q, uint32_t nof_sf, const float *d_in, size_t in_stride,
                           float *d_out, size_t out_stride) {
   if (!q || !d_in || !d_out) return -1;

@@ -26,6 +26,32 @@ __device__ __forceinline__ cf mul_mi(cf a) { return {a.y, -a.x}; } // a * (-i)
 
 #define OFDM_MAXN 2048
 
+// Sample formats of the time-domain input (SRSGPU_SAMPLES_* of srsgpu/ofdm_batch.h). Integer samples
+// become floats in the load of the first FFT stage: (float)v * in_scale as a multiply rounded on its
+// own (__fmul_rn is never contracted into the butterfly's add), so the grid has the bits of a
+// conversion pass in front of the FFT without that pass's 8 B per sample through HBM and back.
+// A symbol starts cp0 + l (N + cp) samples into its row, which is aligned to one sample and no more
+// (N = 128: sample 10, byte 20 of an SC8 row), so each sample is one 16- or 32-bit load; consecutive
+// lanes take consecutive samples.
+enum { FMT_CF32 = 0, FMT_SC16 = 1, FMT_SC8 = 2 };
+template <int FMT> constexpr size_t sample_bytes() { return FMT == FMT_SC8 ? 2 : FMT == FMT_SC16 ? 4 : 8; }
+template <int FMT> __device__ __forceinline__ cf load_sample(const void *__restrict__ src, int i, float in_scale) {
+  if constexpr (FMT == FMT_SC16) {
+    const uint32_t w = ((const uint32_t *)src)[i];
+    return {__fmul_rn((float)(int16_t)(w & 0xffff), in_scale), __fmul_rn((float)(int16_t)(w >> 16), in_scale)};
+  } else if constexpr (FMT == FMT_SC8) {
+    const uint32_t w = ((const uint16_t *)src)[i];
+    return {__fmul_rn((float)(int8_t)(w & 0xff), in_scale), __fmul_rn((float)(int8_t)(w >> 8), in_scale)};
+  } else {
+    return ((const cf *)src)[i];
+  }
+}
+// the samples of subframe sf: row sf of the table if there is one, else in + sf * in_stride samples
+template <int FMT>
+__device__ __forceinline__ const char *sf_row(const void *in, size_t in_stride, const void *const *rows, int sf) {
+  return rows ? (const char *)rows[sf] : (const char *)in + (size_t)sf * in_stride * sample_bytes<FMT>();
+}
+
 // one Stockham radix-R pass: d1[(j/Ns) Ns R + j%Ns + r Ns] = DFT_R(tw^(r k) d0[j + r N/R])
 template <int R>
 __device__ __forceinline__ void stage(const cf *__restrict__ d0, cf *__restrict__ d1, int N, int Ns,
@@ -70,7 +96,9 @@ __device__ __forceinline__ void stage(const cf *__restrict__ d0, cf *__restrict_
   }
 }
 
-__global__ __launch_bounds__(256) void k_ofdm_rx(const float2 *__restrict__ in, size_t in_stride,
+template <int FMT>
+__global__ __launch_bounds__(256) void k_ofdm_rx(const void *__restrict__ in, size_t in_stride,
+                                                 const void *const *__restrict__ rows, float in_scale,
                                                  float2 *__restrict__ out, size_t out_stride, int N,
                                                  int nre, int cp0, int cp, int ns, const float2 *__restrict__ tw,
                                                  const uint32_t radices, int nstages, float scale) {
@@ -79,8 +107,8 @@ __global__ __launch_bounds__(256) void k_ofdm_rx(const float2 *__restrict__ in, 
   const int slot = sym / ns, l = sym % ns;
   // symbol start: slot * 7.5 N + cp0 + l * (N + cp)   (ofdm.c:98-103 guru plan strides)
   const size_t start = (size_t)slot * (N * 15 / 2) + cp0 + (size_t)l * (N + cp);
-  const cf *src = (const cf *)(in + (size_t)sf * in_stride + start);
-  for (int n = threadIdx.x; n < N; n += blockDim.x) buf[0][n] = src[n];
+  const char *src = sf_row<FMT>(in, in_stride, rows, sf) + start * sample_bytes<FMT>();
+  for (int n = threadIdx.x; n < N; n += blockDim.x) buf[0][n] = load_sample<FMT>(src, n, in_scale);
   __syncthreads();
   int cur = 0, Ns = 1;
   for (int st = 0; st < nstages; st++) {
@@ -172,9 +200,9 @@ template <int N> constexpr int lds_slots() { return N + N / 16; }
 // TWC: twiddles from the hardware sine / cosine (v_sin_f32 / v_cos_f32 take the angle in revolutions,
 // here -r k / (Ns R) exactly for the power-of-two stages) instead of loads from the table: no L2 round
 // trip between a stage's LDS reads and its butterflies. Results within a few ulp of the table's.
-template <int R, int N, int Ns, int TPS, bool FIRST, bool TWC = false>
-__device__ __forceinline__ void stage_ip(const cf *__restrict__ src, cf *buf, const float2 *__restrict__ tw,
-                                         int t, bool live) {
+template <int R, int N, int Ns, int TPS, bool FIRST, bool TWC = false, int FMT = FMT_CF32>
+__device__ __forceinline__ void stage_ip(const void *__restrict__ src, cf *buf, const float2 *__restrict__ tw,
+                                         int t, bool live, float in_scale = 1.0f) {
   constexpr int nb = N / R;
   constexpr int NPT = (nb + TPS - 1) / TPS;
   cf v[NPT][R];
@@ -187,7 +215,7 @@ __device__ __forceinline__ void stage_ip(const cf *__restrict__ src, cf *buf, co
       cf a = {0.f, 0.f};
       if (j < nb) {
         if (FIRST) {
-          if (live) a = src[j + r * nb];
+          if (live) a = load_sample<FMT>(src, j + r * nb, in_scale);
         } else {
           a = buf[lpad(j + r * nb)];
           if (Ns > 1 && r) { // e^{-2 pi i r k / (Ns R)} = tw[r k N / (Ns R)]
@@ -220,14 +248,14 @@ __device__ __forceinline__ void stage_ip(const cf *__restrict__ src, cf *buf, co
 }
 
 // stages Ns .. N in place (radix 8 first, then 4, 2, 3); the result is left in buf
-template <int N, int Ns, int TPS, bool TWC = false>
-__device__ __forceinline__ void fft_ip(const cf *__restrict__ src, cf *buf, const float2 *__restrict__ tw,
-                                       int t, bool live) {
+template <int N, int Ns, int TPS, bool TWC = false, int FMT = FMT_CF32>
+__device__ __forceinline__ void fft_ip(const void *__restrict__ src, cf *buf, const float2 *__restrict__ tw,
+                                       int t, bool live, float in_scale = 1.0f) {
   if constexpr (Ns < N) {
     constexpr int rem = N / Ns;
     constexpr int R = rem % 8 == 0 ? 8 : rem % 4 == 0 ? 4 : rem % 2 == 0 ? 2 : 3;
-    stage_ip<R, N, Ns, TPS, Ns == 1, TWC>(src, buf, tw, t, live);
-    fft_ip<N, Ns * R, TPS, TWC>(src, buf, tw, t, live);
+    stage_ip<R, N, Ns, TPS, Ns == 1, TWC, FMT>(src, buf, tw, t, live, in_scale);
+    fft_ip<N, Ns * R, TPS, TWC, FMT>(src, buf, tw, t, live, in_scale);
   }
 }
 
@@ -236,8 +264,9 @@ constexpr int syms_per_wg() {
   return N >= 1024 ? 1 : N >= 512 ? 2 : N >= 256 ? 4 : 8;
 }
 
-template <int N, bool TWC>
-__global__ __launch_bounds__(256) void k_ofdm_rx_c(const float2 *__restrict__ in, size_t in_stride,
+template <int N, bool TWC, int FMT>
+__global__ __launch_bounds__(256) void k_ofdm_rx_c(const void *__restrict__ in, size_t in_stride,
+                                                   const void *const *__restrict__ rows, float in_scale,
                                                    float2 *__restrict__ out, size_t out_stride, int nsym,
                                                    int nre, int cp0, int cp, int ns,
                                                    const float2 *__restrict__ tw, float scale) {
@@ -249,8 +278,8 @@ __global__ __launch_bounds__(256) void k_ofdm_rx_c(const float2 *__restrict__ in
   const int sym = g % (2 * ns), sf = g / (2 * ns);
   const int slot = sym / ns, l = sym % ns;
   const size_t start = (size_t)slot * (N * 15 / 2) + cp0 + (size_t)l * (N + cp);
-  const cf *src = (const cf *)(in + (size_t)(live ? sf : 0) * in_stride + start);
-  fft_ip<N, 1, TPS, TWC>(src, buf[s], tw, t, live);
+  const char *src = sf_row<FMT>(in, in_stride, rows, live ? sf : 0) + start * sample_bytes<FMT>();
+  fft_ip<N, 1, TPS, TWC, FMT>(src, buf[s], tw, t, live, in_scale);
   const cf *res = buf[s];
   if (live) {
     cf *dst = (cf *)(out + (size_t)sf * out_stride + (size_t)sym * nre);
@@ -352,9 +381,29 @@ static void cp_layout(int N, bool ext, int &cp0, int &cp, int &ns) {
   }
 }
 
-hipError_t launch_ofdm_rx(const float2 *in, size_t in_stride, float2 *out, size_t out_stride, int nsf,
-                          int N, int nre, const float2 *tw, uint32_t radices, int nstages, float scale,
-                          bool ext_cp, hipStream_t st) {
+// one symbol (or syms_per_wg) per workgroup at a fixed size, by twiddle source and sample format
+template <int N, bool TWC>
+static void launch_rx_c(int fmt, const void *in, size_t in_stride, const void *const *rows, float in_scale,
+                        float2 *out, size_t out_stride, int nsym, int nre, int cp0, int cp, int ns, const float2 *tw,
+                        float scale, hipStream_t st) {
+  const dim3 grid((unsigned)((nsym + syms_per_wg<N>() - 1) / syms_per_wg<N>()));
+#define OFDM_RX_C(f)                                                                               \
+  hipLaunchKernelGGL((k_ofdm_rx_c<N, TWC, f>), grid, dim3(256), 0, st, in, in_stride, rows, in_scale, out, \
+                     out_stride, nsym, nre, cp0, cp, ns, tw, scale)
+  if (fmt == FMT_SC8)
+    OFDM_RX_C(FMT_SC8);
+  else if (fmt == FMT_SC16)
+    OFDM_RX_C(FMT_SC16);
+  else
+    OFDM_RX_C(FMT_CF32);
+#undef OFDM_RX_C
+}
+
+// nsf subframes of samples in format fmt: subframe i at rows[i] when rows is given (a device array of
+// device-readable pointers), else at in + i * in_stride complex floats
+static hipError_t launch_rx(const float2 *in, size_t in_stride, const void *const *rows, int fmt, float in_scale,
+                            float2 *out, size_t out_stride, int nsf, int N, int nre, const float2 *tw,
+                            uint32_t radices, int nstages, float scale, bool ext_cp, hipStream_t st) {
   if (nsf <= 0) return hipSuccess;
   int cp0, cp, ns;
   cp_layout(N, ext_cp, cp0, cp, ns);
@@ -362,12 +411,12 @@ hipError_t launch_ofdm_rx(const float2 *in, size_t in_stride, float2 *out, size_
   // SRSGPU_OFDM_PERSIST=1: the resident-grid kernel with next-symbol prefetch for the large sizes.
   // Off by default: alone on the GPU it took 68 us per 512 20 MHz subframes against 59 us for one
   // symbol per workgroup (profiles/r04_s6_kb_*.json), and its fixed grid fares worse still beside
-  // another stream's kernels.
+  // another stream's kernels. Strided complex floats only: a row table never takes it.
   static const bool persist = [] {
     const char *e = getenv("SRSGPU_OFDM_PERSIST");
     return e && e[0] == '1';
   }();
-  if (persist && (N == 2048 || N == 1536 || N == 1024)) {
+  if (persist && !rows && (N == 2048 || N == 1536 || N == 1024)) {
     // every workgroup takes the same number of symbols (no partial last round)
 #define OFDM_RX_P(n)                                                                               \
   if (N == n) {                                                                                    \
@@ -391,11 +440,11 @@ hipError_t launch_ofdm_rx(const float2 *in, size_t in_stride, float2 *out, size_
 #define OFDM_RX_C(n)                                                                               \
   case n:                                                                                          \
     if (twc)                                                                                       \
-      hipLaunchKernelGGL((k_ofdm_rx_c<n, true>), dim3((unsigned)((nsym + syms_per_wg<n>() - 1) / syms_per_wg<n>())), \
-                         dim3(256), 0, st, in, in_stride, out, out_stride, nsym, nre, cp0, cp, ns, tw, scale); \
+      launch_rx_c<n, true>(fmt, in, in_stride, rows, in_scale, out, out_stride, nsym, nre, cp0, cp, ns, tw, scale, \
+                           st);                                                                    \
     else                                                                                           \
-      hipLaunchKernelGGL((k_ofdm_rx_c<n, false>), dim3((unsigned)((nsym + syms_per_wg<n>() - 1) / syms_per_wg<n>())), \
-                         dim3(256), 0, st, in, in_stride, out, out_stride, nsym, nre, cp0, cp, ns, tw, scale); \
+      launch_rx_c<n, false>(fmt, in, in_stride, rows, in_scale, out, out_stride, nsym, nre, cp0, cp, ns, tw, scale, \
+                            st);                                                                   \
     return hipGetLastError();
   switch (N) {
     OFDM_RX_C(128)
@@ -410,9 +459,32 @@ hipError_t launch_ofdm_rx(const float2 *in, size_t in_stride, float2 *out, size_
     break;
   }
 #undef OFDM_RX_C
-  hipLaunchKernelGGL(k_ofdm_rx, dim3((unsigned)nsym), dim3(256), 0, st, in, in_stride, out, out_stride,
-                     N, nre, cp0, cp, ns, tw, radices, nstages, scale);
+#define OFDM_RX_G(f)                                                                               \
+  hipLaunchKernelGGL(k_ofdm_rx<f>, dim3((unsigned)nsym), dim3(256), 0, st, in, in_stride, rows, in_scale, out, \
+                     out_stride, N, nre, cp0, cp, ns, tw, radices, nstages, scale)
+  if (fmt == FMT_SC8)
+    OFDM_RX_G(FMT_SC8);
+  else if (fmt == FMT_SC16)
+    OFDM_RX_G(FMT_SC16);
+  else
+    OFDM_RX_G(FMT_CF32);
+#undef OFDM_RX_G
   return hipGetLastError();
+}
+
+hipError_t launch_ofdm_rx(const float2 *in, size_t in_stride, float2 *out, size_t out_stride, int nsf,
+                          int N, int nre, const float2 *tw, uint32_t radices, int nstages, float scale,
+                          bool ext_cp, hipStream_t st) {
+  return launch_rx(in, in_stride, nullptr, FMT_CF32, 1.0f, out, out_stride, nsf, N, nre, tw, radices, nstages, scale,
+                   ext_cp, st);
+}
+
+hipError_t launch_ofdm_rx_rows(const void *const *rows, int fmt, float in_scale, float2 *out, size_t out_stride,
+                               int nsf, int N, int nre, const float2 *tw, uint32_t radices, int nstages, float scale,
+                               bool ext_cp, hipStream_t st) {
+  if (fmt < FMT_CF32 || fmt > FMT_SC8) return hipErrorInvalidValue;
+  return launch_rx(nullptr, 0, rows, fmt, in_scale, out, out_stride, nsf, N, nre, tw, radices, nstages, scale, ext_cp,
+                   st);
 }
 
 // srslte_ofdm_tx_sf (ofdm.c:491-598), normal CP: per symbol the grid row goes to bins

@@ -105,14 +105,29 @@ __global__ void k_noise_gather(const float *__restrict__ noise, const uint32_t *
 // Ingest of one batch's time-domain samples into the slot's device buffer (dst: [item][antenna] rows of
 // `row` complex floats). src[r] is a device-visible pointer to row r's samples: host memory the caller
 // registered (srsgpu_rxq_register, read over PCIe by the GPU: no host copy, no per-item DMA call) or the
-// slot's raw staging buffer. sc16: int16 I/Q pairs scaled by `scale` (the radio's native format, half the
-// PCIe bytes), else complex floats. Rows with a null src were staged by the DMA already.
+// slot's raw staging buffer. fmt SC16: int16 I/Q pairs scaled by `scale` (the radio's native format, half
+// the PCIe bytes); SC8: int8 I/Q pairs (a quarter); else complex floats. Rows with a null src were staged
+// by the DMA already.
 __global__ __launch_bounds__(256) void k_ingest(const void *const *__restrict__ src, int nrows, size_t row,
-                                                int sc16, float scale, float2 *__restrict__ dst) {
+                                                int fmt, float scale, float2 *__restrict__ dst) {
   const int r = blockIdx.y;
   if (r >= nrows || !src[r]) return;
   float2 *d = dst + (size_t)r * row;
-  if (sc16) {
+  if (fmt == SRSGPU_RXQ_SC8) {
+    const uint4 *s4 = (const uint4 *)src[r]; // 8 samples per 16 B
+    const size_t n8 = row / 8;
+    for (size_t i = blockIdx.x * 256 + threadIdx.x; i < n8; i += (size_t)gridDim.x * 256) {
+      const uint4 v = s4[i];
+      const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+      float4 *o = (float4 *)(d + 8 * i);
+#pragma unroll
+      for (int k = 0; k < 4; k++) { // the product rounded on its own, as the OFDM load's (ofdm_kernels.hip)
+        const uint32_t a = w[k];
+        o[k] = make_float4(__fmul_rn((float)(int8_t)(a & 0xff), scale), __fmul_rn((float)(int8_t)((a >> 8) & 0xff), scale),
+                           __fmul_rn((float)(int8_t)((a >> 16) & 0xff), scale), __fmul_rn((float)(int8_t)(a >> 24), scale));
+      }
+    }
+  } else if (fmt == SRSGPU_RXQ_SC16) {
     const uint4 *s4 = (const uint4 *)src[r]; // 4 samples per 16 B
     const size_t n4 = row / 4;
     for (size_t i = blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
@@ -246,7 +261,7 @@ struct srsgpu_rxq {
   int nslot = 3; // slots in use (SRSGPU_RXQ_SLOTS, 3 or 4)
   struct Slot {
     float *h_td = nullptr, *d_td = nullptr; // pinned staging (raw format) / device samples (cf32)
-    float *d_raw = nullptr;                  // SC16: the staged raw samples before conversion
+    float *d_raw = nullptr;                  // SC16 / SC8: the staged raw samples before conversion
     const void **h_src = nullptr, **d_src = nullptr; // per row: registered host source (device view) or null
     std::vector<const void *> h_host;                // per row: the registered host pointer itself
     std::vector<const char *> h_rgn;                 // per row: the start of its registered region
@@ -256,8 +271,9 @@ struct srsgpu_rxq {
     int state = FILLING;
     int copying = 0; // submitters still copying their samples in
     uint32_t nstaged = 0; // items whose samples went through the staging buffer
-    int sc16 = 0;          // the input format of this slot's items (set with its first item)
-    float sc16_scale = 1.0f / 32768.0f;
+    uint32_t fmt = SRSGPU_RXQ_CF32; // the input format of this slot's items (set with its first item)
+    float in_scale = 1.0f;          // integer formats: sample value = (float)v * in_scale
+    bool fused = false;             // integer rows go to the OFDM kernel as they are (stage() decides)
     // the batch's pinned host inputs of H2D copies and its results (per slot: the next batch is
     // prepared while this one's copies may still be in flight)
     uint8_t *h_est = nullptr;
@@ -281,8 +297,14 @@ struct srsgpu_rxq {
     size_t staged_bytes = 0;
   } slot[NSLOT];
   // input format (srsgpu_rxq_set_input_format) and caller memory the GPU reads directly
-  int sc16 = 0; // guarded by m; a change waits until nothing is queued and holds new submissions
-  float sc16_scale = 1.0f / 32768.0f;
+  uint32_t fmt = SRSGPU_RXQ_CF32; // guarded by m; a change waits until nothing is queued and holds new submissions
+  float in_scale = 1.0f;
+  // Integer formats the OFDM kernel converts in its own first load (srsgpu_ofdm_rx_sf_rows_dev on the
+  // slot's row table) instead of k_ingest writing complex floats to d_td for it to read back: bit f set =
+  // format f fused. SRSGPU_RXQ_FUSE unset: SC8 only (SC16 keeps the path it always had); 0: none; 1: SC8
+  // and SC16. Both paths give the same bits.
+  uint32_t fuse_mask = 1u << SRSGPU_RXQ_SC8;
+  static size_t sample_bytes(uint32_t f) { return f == SRSGPU_RXQ_SC8 ? 2 : f == SRSGPU_RXQ_SC16 ? 4 : 8; }
   bool fmt_busy = false;
   struct Region {
     const char *h;
@@ -373,7 +395,7 @@ struct srsgpu_rxq {
     for (int k = 0; k < nslot; k++) {
       Slot &s = slot[k];
       RXQ_CHK(hipMalloc(&s.d_td, sizeof(float) * 2 * td_len * mb * nrx));
-      RXQ_CHK(hipMalloc(&s.d_raw, sizeof(float) * td_len * mb * nrx)); // SC16 rows: 4 B per sample
+      RXQ_CHK(hipMalloc(&s.d_raw, sizeof(float) * td_len * mb * nrx)); // SC16 rows: 4 B per sample (SC8: 2)
       RXQ_CHK(hipHostMalloc(&s.h_td, sizeof(float) * 2 * td_len * mb * nrx));
       RXQ_CHK(hipHostMalloc(&s.h_src, sizeof(void *) * mb * nrx));
       RXQ_CHK(hipMalloc(&s.d_src, sizeof(void *) * mb * nrx));
@@ -424,6 +446,8 @@ struct srsgpu_rxq {
     srsgpu_pcfich_set_noise_dev(pcfich, d_uenoise);
     if (const char *e = getenv("SRSGPU_RXQ_INGEST")) ingest_dma = strcmp(e, "kernel") != 0;
     if (const char *e = getenv("SRSGPU_RXQ_WAKE_ALL")) wake_all = e[0] == '1';
+    if (const char *e = getenv("SRSGPU_RXQ_FUSE"))
+      fuse_mask = e[0] == '1' ? (1u << SRSGPU_RXQ_SC8) | (1u << SRSGPU_RXQ_SC16) : e[0] == '0' ? 0u : fuse_mask;
     closer = std::thread([this] { close_loop(); });
     worker = std::thread([this] { run_loop(); });
     completer = std::thread([this] { comp_loop(); });
@@ -501,10 +525,10 @@ struct srsgpu_rxq {
       s = fill;
       idx = (int)slot[s].items.size();
       if (idx == 0) { // the slot's format: every item of it is submitted under the same one
-        slot[s].sc16 = sc16;
-        slot[s].sc16_scale = sc16_scale;
+        slot[s].fmt = fmt;
+        slot[s].in_scale = in_scale;
       }
-      row_bytes = (slot[s].sc16 ? 4 : 8) * td_len;
+      row_bytes = sample_bytes(slot[s].fmt) * td_len;
       *ticket = next_ticket++;
       slot[s].items.push_back({it, ue, *ticket, std::chrono::steady_clock::now()});
       for (uint32_t a = 0; a < nrx; a++) {
@@ -537,11 +561,16 @@ struct srsgpu_rxq {
   // the closed slot's samples to the device: one DMA of the staged rows' region (up to the last staged
   // row); registered rows either by DMA straight from the caller's memory into d_reg, one copy per run
   // of rows contiguous there (ingest_dma), or read over the bus by the ingest kernel; the ingest kernel
-  // then converts SC16 rows and moves registered rows into place. The staged DMA may cover registered
+  // then converts SC16 / SC8 rows and moves registered rows into place. The staged DMA may cover registered
   // rows' places with stale staging bytes: the ingest kernel writes them after it on the same stream.
+  // A fused slot (integer rows of a format in fuse_mask) launches no ingest kernel: its row table goes
+  // up with every row's address (in d_raw, in d_reg, or the caller's memory with SRSGPU_RXQ_INGEST=kernel)
+  // and the OFDM kernel reads the raw rows through it; table and rows are the slot's until it is free again.
   bool stage(Slot &sl, size_t n) {
-    const int sc16 = sl.sc16;
-    const size_t rows = n * nrx, row_bytes = (sc16 ? 4 : 8) * td_len;
+    const uint32_t fmt = sl.fmt;
+    const bool raw = fmt != SRSGPU_RXQ_CF32;
+    sl.fused = raw && ((fuse_mask >> fmt) & 1u);
+    const size_t rows = n * nrx, row_bytes = sample_bytes(fmt) * td_len;
     size_t last = 0, nst = 0;
     for (size_t r = 0; r < rows; r++)
       if (!sl.h_src[r]) {
@@ -549,7 +578,7 @@ struct srsgpu_rxq {
         nst++;
       }
     sl.nstaged = (uint32_t)nst;
-    char *dst_raw = sc16 ? (char *)sl.d_raw : (char *)sl.d_td;
+    char *dst_raw = raw ? (char *)sl.d_raw : (char *)sl.d_td;
     if (last && hipMemcpyAsync(dst_raw, sl.h_td, last * row_bytes, hipMemcpyHostToDevice, cst) != hipSuccess)
       return false;
     if (ingest_dma) {
@@ -591,17 +620,19 @@ struct srsgpu_rxq {
       }
       if (!flush_span()) return false;
     }
-    const bool kernel = sc16 || nst < rows;
+    const bool kernel = raw || nst < rows;
     if (kernel) {
-      // staged rows: SC16 converts from the raw copy, cf32 is in place
+      // staged rows: integer formats convert from the raw copy, cf32 is in place
       for (size_t r = 0; r < rows; r++)
-        if (!sl.h_src[r]) sl.h_src[r] = sc16 ? (const void *)(dst_raw + r * row_bytes) : nullptr;
+        if (!sl.h_src[r]) sl.h_src[r] = raw ? (const void *)(dst_raw + r * row_bytes) : nullptr;
       if (xfer(sl.d_src, sl.h_src, sizeof(void *) * rows, hipMemcpyHostToDevice, cst) != hipSuccess)
         return false;
-      const unsigned gx = (unsigned)std::min<size_t>(64, (td_len / 2 + 255) / 256);
-      hipLaunchKernelGGL(k_ingest, dim3(gx, (unsigned)rows), dim3(256), 0, cst, (const void *const *)sl.d_src,
-                         (int)rows, td_len, sc16, sl.sc16_scale, (float2 *)sl.d_td);
-      if (hipGetLastError() != hipSuccess) return false;
+      if (!sl.fused) {
+        const unsigned gx = (unsigned)std::min<size_t>(64, (td_len / 2 + 255) / 256);
+        hipLaunchKernelGGL(k_ingest, dim3(gx, (unsigned)rows), dim3(256), 0, cst, (const void *const *)sl.d_src,
+                           (int)rows, td_len, (int)fmt, sl.in_scale, (float2 *)sl.d_td);
+        if (hipGetLastError() != hipSuccess) return false;
+      }
     }
     zero_copy_rows += rows - nst;
     staged_rows += nst;
@@ -912,7 +943,10 @@ struct srsgpu_rxq {
     };
     rs_slot.clear();
     rs_ncb.clear();
-    if (srsgpu_ofdm_rx_sf_dev(ofdm, n * nrx, d_td, td_len, d_grid, gsz)) return -1;
+    if (sl.fused ? srsgpu_ofdm_rx_sf_rows_dev(ofdm, n * nrx, (const void *const *)sl.d_src, sl.fmt, sl.in_scale,
+                                              d_grid, gsz)
+                 : srsgpu_ofdm_rx_sf_dev(ofdm, n * nrx, d_td, td_len, d_grid, gsz))
+      return -1;
     std::vector<uint32_t> sfi(n * nrx);
     for (uint32_t i = 0; i < n; i++)
       for (uint32_t a = 0; a < nrx; a++) sfi[i * nrx + a] = b[i].sf_idx();
@@ -1276,14 +1310,15 @@ int srsgpu_rxq_free_host(srsgpu_rxq_t *q, void *host) {
 }
 
 int srsgpu_rxq_set_input_format(srsgpu_rxq_t *q, uint32_t format, float scale) {
-  if (!q || format > SRSGPU_RXQ_SC16) return -1;
+  if (!q || format > SRSGPU_RXQ_SC8) return -1;
+  if (format == SRSGPU_RXQ_SC8 && q->N % 8) return -1; // rows of 30 N bytes: 16-byte multiples only then
   {
     std::unique_lock<std::mutex> l(q->m);
     q->cv_done.wait(l, [&] { return !q->fmt_busy; });
     q->fmt_busy = true; // new submissions wait; the queued ones drain under the old format
     q->cv_done.wait(l, [&] { return q->done_upto + 1 >= q->next_ticket; });
-    q->sc16 = format == SRSGPU_RXQ_SC16;
-    q->sc16_scale = scale != 0.f ? scale : 1.0f / 32768.0f;
+    q->fmt = format;
+    q->in_scale = scale != 0.f ? scale : format == SRSGPU_RXQ_SC8 ? 1.0f / 128.0f : 1.0f / 32768.0f;
     q->fmt_busy = false;
   }
   q->cv_slot.notify_all();

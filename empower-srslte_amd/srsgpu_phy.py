@@ -443,6 +443,7 @@ _sig = {
     "srsgpu_ofdm_rx_set_normalize": (None, [_vp, _i32]),
     "srsgpu_ofdm_set_cp": (_i32, [_vp, _u32]),
     "srsgpu_ofdm_rx_sf_dev": (_i32, [_vp, _u32, _vp, _sz, _vp, _sz]),
+    "srsgpu_ofdm_rx_sf_rows_dev": (_i32, [_vp, _u32, _vp, _u32, ctypes.c_float, _vp, _sz]),
     "srsgpu_ofdm_tx_sf_dev": (_i32, [_vp, _u32, _vp, _sz, _vp, _sz]),
     "srsgpu_chest_put_crs_dev": (_i32, [_vp, _u32p, _u32, _vp, _sz]),
     "srsgpu_pdsch_encode_ports_dev": (_i32, [_vp, _vp, _u32, _vp, _vp, _sz]),
@@ -1139,6 +1140,13 @@ class OfdmRx:
     def rx_dev(self, n, d_in, in_stride, d_out, out_stride):
         return _lib.srsgpu_ofdm_rx_sf_dev(self.q, n, _vp(d_in), in_stride, _vp(d_out), out_stride)
 
+    CF32, SC16, SC8 = 0, 1, 2  # SRSGPU_SAMPLES_*
+
+    def rx_rows_dev(self, n, d_rows, fmt, in_scale, d_out, out_stride):
+        """srsgpu_ofdm_rx_sf_rows_dev: d_rows is a device array of n device pointers, one per subframe of
+        15 N samples in format fmt; integer samples enter the FFT as float(v) * in_scale"""
+        return _lib.srsgpu_ofdm_rx_sf_rows_dev(self.q, n, _vp(d_rows), fmt, in_scale, _vp(d_out), out_stride)
+
     def tx_dev(self, n, d_in, in_stride, d_out, out_stride):
         """srsgpu_ofdm_tx_sf_dev: grids -> time-domain subframes (same handle)"""
         return _lib.srsgpu_ofdm_tx_sf_dev(self.q, n, _vp(d_in), in_stride, _vp(d_out), out_stride)
@@ -1384,7 +1392,7 @@ class RxQueue:
             raise RuntimeError("srsgpu_rxq_free_host failed")
         self._owned.pop(p, None)
 
-    SC16, CF32 = 1, 0
+    SC8, SC16, CF32 = 2, 1, 0
 
     def set_input_format(self, fmt, scale=0.0):
         if _lib.srsgpu_rxq_set_input_format(self.q, fmt, scale) != 0:

@@ -39,6 +39,20 @@ int srsgpu_ofdm_set_cp(srsgpu_ofdm_t *q, uint32_t cp);
 int srsgpu_ofdm_rx_sf_dev(srsgpu_ofdm_t *q, uint32_t nof_sf, const float *d_in, size_t in_stride,
                           float *d_out, size_t out_stride);
 
+/* The same from a table of raw rows: d_rows is a device array of nof_sf device-readable pointers, each
+ * to one subframe's 15 symbol_sz samples in `format` and 16-byte aligned (the rows may lie anywhere,
+ * in any order). Integer samples are converted in the FFT's first load as (float)v * in_scale, rounded
+ * as a conversion pass in front of srsgpu_ofdm_rx_sf_dev would round them: the grids are bit-identical
+ * to that, without the pass. in_scale is ignored for complex float. Same cyclic prefix,
+ * normalisation, output layout and stream as srsgpu_ofdm_rx_sf_dev; the table and the rows must stay
+ * unchanged until the call's work on the stream has finished. -1: null handle or pointers,
+ * format > SRSGPU_SAMPLES_SC8, short out_stride. The queue's SRSGPU_RXQ_* formats are these values. */
+#define SRSGPU_SAMPLES_CF32 0 /* complex float, 8 B / sample */
+#define SRSGPU_SAMPLES_SC16 1 /* int16 I, int16 Q, 4 B / sample */
+#define SRSGPU_SAMPLES_SC8 2  /* int8 I, int8 Q, 2 B / sample */
+int srsgpu_ofdm_rx_sf_rows_dev(srsgpu_ofdm_t *q, uint32_t nof_sf, const void *const *d_rows, uint32_t format,
+                               float in_scale, float *d_out, size_t out_stride);
+
 /* Transmit direction on the same handle (srslte_ofdm_tx_sf, ofdm.c:491-598; tx plans are
  * unnormalised by default, ofdm.c:276; srsgpu_ofdm_rx_set_normalize applies 1/sqrt(N) here too):
  * grid i at d_in + i*in_stride (14 x 12 nof_prb) -> 15 symbol_sz samples with CPs at

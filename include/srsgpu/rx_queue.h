@@ -39,7 +39,7 @@ typedef struct {
   /* in */
   const void *td[2];        /* host time-domain subframe per rx antenna: 15 * symbol_sz complex
                                float samples (srslte_ofdm_rx_sf's input, cyclic prefixes included;
-                               int16 I/Q pairs with SRSGPU_RXQ_SC16) */
+                               int16 I/Q pairs with SRSGPU_RXQ_SC16, int8 pairs with SRSGPU_RXQ_SC8) */
   srsgpu_pdsch_sf_t sf;     /* the grant; grid_offset / ce_offset / data_offset are the queue's */
   uint32_t reset_softbuffer[2]; /* new transport block: srslte_softbuffer_rx_reset first */
   uint8_t *data[2];         /* host output per TB: SRSGPU_DLSCH_DATA_LEN(tbs) bytes */
@@ -149,11 +149,18 @@ int srsgpu_rxq_unregister(srsgpu_rxq_t *q, void *host);
  * frees it; blocks not freed are freed by srsgpu_rxq_destroy. */
 void *srsgpu_rxq_alloc_host(srsgpu_rxq_t *q, size_t bytes);
 int srsgpu_rxq_free_host(srsgpu_rxq_t *q, void *host);
-/* Sample format of every td buffer: complex float (default; srslte_ofdm_rx_sf's input) or the radio's
- * int16 I/Q pairs (4 bytes per sample, half the PCIe bytes), converted on the GPU as value * scale
- * (0: 1 / 32768, UHD's sc16 -> fc32). Waits until nothing is queued. */
+/* Sample format of every td buffer: complex float (default; srslte_ofdm_rx_sf's input), the radio's
+ * int16 I/Q pairs (4 bytes per sample, half the PCIe bytes) or int8 I/Q pairs (UHD's sc8 wire format,
+ * 2 bytes per sample, a quarter; symbol_sz must be a multiple of 8), converted on the GPU as
+ * value * scale (0: 1 / 32768 for SC16, UHD's sc16 -> fc32, and 1 / 128 for SC8). The values are those
+ * of SRSGPU_SAMPLES_* (ofdm_batch.h). Waits until nothing is queued.
+ * SC8 rows are converted in the OFDM kernel's own first load (srsgpu_ofdm_rx_sf_rows_dev): no
+ * conversion kernel, no complex-float copy of the batch in HBM. SRSGPU_RXQ_FUSE=1 does the same for
+ * SC16, SRSGPU_RXQ_FUSE=0 converts every format in the ingest kernel first; the results are the same
+ * bits either way. */
 #define SRSGPU_RXQ_CF32 0
 #define SRSGPU_RXQ_SC16 1
+#define SRSGPU_RXQ_SC8 2
 int srsgpu_rxq_set_input_format(srsgpu_rxq_t *q, uint32_t format, float scale);
 /* antenna rows ingested so far: read from registered memory / staged by a host copy */
 void srsgpu_rxq_ingest_stats(srsgpu_rxq_t *q, uint64_t *zero_copy_rows, uint64_t *staged_rows);
