@@ -167,6 +167,14 @@ uint32_t srsgpu_tdec_input_len(int impl, int sb_layout, uint32_t K) {
   return sb ? 3 * (K + 32) + 12 : 3 * K + 12;
 }
 
+int srsgpu_tdec_latency_form(int impl, uint32_t K) {
+  if (cb_index(K) < 0) return -1;
+  if ((impl < SRSLTE_TDEC_AUTO || impl > SRSLTE_TDEC_AVX8_WINDOW) && impl != SRSGPU_TDEC_AUTO_8BIT) return -1;
+  const int r = resolve_impl(impl, K), nb = impl_nb(r);
+  if (nb > 1 && (K % nb || K / nb <= 40)) return -1; // a size the window decoder refuses (check_spec)
+  return srsgpu::knobs().spread && srsgpu::spread_ok(Engine::kind_of(r), (int)K, nb) ? 1 : 0;
+}
+
 int srsgpu_tdec_batch_create(srsgpu_tdec_batch_t **q, uint32_t max_cbs, uint32_t max_long_cb) {
   if (!q) return -1;
   auto *b = new srsgpu_tdec_batch();
@@ -440,8 +448,8 @@ static int tdec_gpu_decide(srslte_tdec_t *h, uint8_t *output) {
 }
 
 // one half-iteration and its decision bytes (the srslte_tdec_iteration protocol): one k_win_spread
-// launch that also writes the bytes into the handle's mapped host buffer when the block allows it
-// (windowed kind, K / nb a multiple of 16), else the half-iteration, k_decide and a copy
+// launch that also writes the bytes into the handle's mapped host buffer for every size a windowed
+// kind decodes, else (SSE / generic kinds, SRSGPU_SPREAD=0) the half-iteration, k_decide and a copy
 static int tdec_gpu_step(srslte_tdec_t *h, const int16_t *input, int impl, uint8_t *output) {
   auto *g = (TdecGpu *)h->gpu;
   Engine &e = g->e;

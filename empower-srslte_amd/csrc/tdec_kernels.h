@@ -81,13 +81,13 @@ int dec_words_host(int K, int nb);
 hipError_t launch_halfit(int n, int kind, const TdGroup *dg, int ng, int nblocks, size_t lds,
                          bool dec, const TdArrays &a, const uint8_t *pair_done, hipStream_t st);
 // the same for ONE group of at most spread_max_pairs() pairs as k_win_spread (latency form), when
-// spread_ok(kind, K, nb): a windowed kind with K / nb a multiple of 16 and at least 48
+// spread_ok(kind, K, nb): every size a windowed kind decodes (nb > 1, K % nb == 0, K / nb > 40)
 int spread_max_pairs();
 bool spread_ok(int kind, int K, int nb);
 // outb (dec only): the decision bytes of every block of the group also written by the same launch,
 // row cb0 + c at outb + (cb0 + c) * out_stride (k_decide's fixed-iteration output)
 // cnt: per-pair arrival counters of the pair's workgroups (zeroed, left zeroed; needed with outb);
-// flag (optional, host-mapped): seq is stored there once the bytes are written
+// flag (optional, host-mapped, one-pair launches only): seq is stored there once the bytes are written
 struct SpreadOut {
   uint32_t *cnt = nullptr, *flag = nullptr;
   uint32_t seq = 0;

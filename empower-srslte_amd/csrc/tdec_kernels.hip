@@ -1063,7 +1063,14 @@ __global__ __launch_bounds__(128, MODE == 2 ? TD_H0_WAVES : TD_BIDIR_WAVES) void
 // The serial chain becomes L + 40 steps of one recursion plus two chunk tasks. Same steps, same
 // normalisation schedule and same checkpoint values as k_win_bidir, so the output is identical
 // (tests: every batch of one pair goes through here, larger ones through k_win_bidir).
-// Needs L = K / NB a multiple of 16 (no partial chunk) and nc >= 3 (spread_ok).
+// Takes every L = K / NB > 40 (spread_ok), so nc = ceil(L / 16) >= 3. When L is not a multiple of
+// 16 the top chunk holds n = L - 16 (nc - 1) steps: phase A's beta wave runs those n steps down from
+// beta[L] (wave-uniform guards), its alpha wave only checkpoints the state entering that chunk, and
+// phase B's tasks of the top chunk — in the same waves as full ones — take their betas by selects
+// (as win_bidir_body's partial chunk), discard the stores of steps >= n through the buffer range
+// check and mask those steps' decision bits. Loads never pass the chain's last T4 group. All of that
+// is the PART instantiation; as launch-uniform branches of one kernel it cost K = 6144 a microsecond
+// a call (DESIGN §5 "Drop-in latency").
 // quad_perm DPP move (within each group of 4 lanes)
 template <int CTRL> __device__ __forceinline__ uint32_t dppq(uint32_t v) {
   return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, CTRL, 0xF, 0xF, true);
@@ -1084,7 +1091,11 @@ template <int CTRL> __device__ __forceinline__ uint32_t dppq(uint32_t v) {
 #endif
 #define TD_SPREAD_MAX_PAIRS 16 // at most this many pairs per job: k_win_bidir beyond
 
-template <int NB, int DIV, int MODE, bool DOUT, bool B8>
+__device__ __forceinline__ uint32_t h0_byte(const uint32_t *dw, int nw, int L, int gap, float invL, int h, int p);
+
+// PART: L is no multiple of 16 (the launcher's choice). The instantiations for whole chunks carry
+// none of the partial chunk's clamps, guards and selects.
+template <int NB, int DIV, int MODE, bool DOUT, bool B8, bool PART>
 __global__ __launch_bounds__(TD_SPREAD_THREADS) void k_win_spread(const TdGroup *__restrict__ groups,
                                                                 const s4 *__restrict__ SP0, s2 *__restrict__ XP1,
                                                                 s2 *__restrict__ Aarr, uint32_t *__restrict__ Darr,
@@ -1099,7 +1110,9 @@ __global__ __launch_bounds__(TD_SPREAD_THREADS) void k_win_spread(const TdGroup 
   const TdGroup &G = groups[0];
   const int K = G.K, pair = blockIdx.x / TD_SPREAD_SPLIT, part = blockIdx.x % TD_SPREAD_SPLIT;
   if (pair_done && pair_done[G.pair0 + pair]) return; // uniform over the workgroup
-  const int L = K / NB, nc = L / CW;
+  const int L = K / NB, nc = PART ? (L + CW - 1) / CW : L / CW;
+  const int ntop = PART ? L - CW * (nc - 1) : CW; // steps of the top chunk
+  const int G4 = (L + 3) >> 2;                    // T4 groups per chain
   const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
   if (wave == 0) SP_T(0);
   const int pe = t4_pair_elems(K, NB);
@@ -1193,8 +1206,26 @@ __global__ __launch_bounds__(TD_SPREAD_THREADS) void k_win_spread(const TdGroup 
     q &= 1; // timing experiment only (wrong results): phase A's chunk loads from two cache-resident chunks
 #endif
 #pragma unroll
-    for (int u = 0; u < 4; u++) ld_grp(c.g[u], 4 * q + u, dd, 0);
+    for (int u = 0; u < 4; u++) ld_grp(c.g[u], PART ? min(4 * q + u, G4 - 1) : 4 * q + u, dd, 0); // uniform clamp into the chain
     __builtin_amdgcn_sched_barrier(0);
+  };
+  // x, y of step k of chain dd by element loads: the alpha prepass when L is not a multiple of 4 (its
+  // 40 steps do not fill whole T4 groups), as win_bidir_body's
+  auto ld_step = [&](int k, int dd, s2 &x, s2 &y) {
+    const uint32_t pos = (uint32_t)(((k >> 2) * NB + dd) * 4 + (k & 3)), sb = (uint32_t)(k * NB + dd);
+    if (MODE == 1) {
+      x = as_s2(bld32(R.x2, 4u * sb, 0));
+      const s2 p = as_s2(bld32(R.p1, 4u * pos, 0));
+      y = B8 ? bscale(p) : p;
+    } else {
+      const s2 sy = as_s2(bld32(R.sp0, 8u * pos, 0)), pa = as_s2(bld32(R.sp0, 8u * pos, 4));
+      const s2 a = MODE == 2 ? splat(0) : as_s2(bld32(R.a, 4u * sb, 0));
+      if (B8)
+        x = MODE == 2 ? bscale(sy) : badd(a, bscale(sy));
+      else
+        x = MODE == 2 ? sy : sadd(a, sy);
+      y = B8 ? bscale(pa) : pa;
+    }
   };
   auto cstep = [&](const Chunk<MODE> &c, int j, s2 &x, s2 &y, s2 &e) {
     grp_step<MODE, B8>(c.g[j >> 2], j & 3, x, y, e);
@@ -1247,7 +1278,7 @@ __global__ __launch_bounds__(TD_SPREAD_THREADS) void k_win_spread(const TdGroup 
     Chunk<MODE> c0, c1, c2;
     if (role == 0) {
       const int dp = d > 0 ? d - 1 : 0;
-      {
+      if (!PART || (L & 3) == 0) {
         Grp<MODE> pg[10];
         const int gp = (L - TD_OVERLAP) >> 2;
 #pragma unroll
@@ -1260,12 +1291,23 @@ __global__ __launch_bounds__(TD_SPREAD_THREADS) void k_win_spread(const TdGroup 
           grp_step<MODE, false>(pg[k >> 2], k & 3, x, y, e);
           qa(v, x, y, (k & 1) == 0 && k != 0);
         }
+      } else { // the last 40 steps of chain d-1 do not start on a T4 group: element loads, 8 steps at a time
+        ld_chunk(c0, 0, d);
+        ld_chunk(c1, 1, d);
+        for (int k0 = 0; k0 < TD_OVERLAP; k0 += 8) {
+          s2 xs[8], ys[8];
+#pragma unroll
+          for (int u = 0; u < 8; u++) ld_step(L - TD_OVERLAP + k0 + u, dp, xs[u], ys[u]);
+#pragma unroll
+          for (int u = 0; u < 8; u++) qa(v, xs[u], ys[u], (u & 1) == 0 && (k0 + u) != 0);
+        }
       }
       if (wave == 0) SP_T(1);
       if (d == 0) v = r == 0 ? (NEG << 16) : (NEG | (NEG << 16)); // state 0 = 0 (win.h:496-500)
       auto fwd_chunk = [&](const Chunk<MODE> &c, int q) {
         ck_at(q, 2 * r) = (short)(v & 0xffffu);
         ck_at(q, 2 * r + 1) = (short)(v >> 16);
+        if (PART && q == nc - 1) return; // the top chunk: only the state entering it is needed
 #pragma unroll
         for (int j = 0; j < CW; j++) {
           s2 x, y, e;
@@ -1321,31 +1363,50 @@ __global__ __launch_bounds__(TD_SPREAD_THREADS) void k_win_spread(const TdGroup 
         ck_at(slot, r + 4) = (short)(v >> 16);
       };
       put_b(2 * nc); // beta[L]
-      auto bwd_chunk = [&](const Chunk<MODE> &c, int q) { // q >= 1
+      auto bwd_chunk = [&](const Chunk<MODE> &c, int q, int n) { // q >= 1; n steps (wave-uniform)
 #pragma unroll
         for (int j = CW - 1; j >= 0; j--) {
-          s2 x, y, e;
-          cstep(c, j, x, y, e);
-          if (j == 0) { // the checkpoint is beta[16 q] before its normalisation
-            qb(v, x, y, false);
-            put_b(nc + q);
-            v = bits(ssub(as_s2(v), s2{as_s2(dppq<0x00>(v)).x, as_s2(dppq<0x00>(v)).x}));
-          } else {
-            qb(v, x, y, (j & 1) == 0);
+          if (j < n) {
+            s2 x, y, e;
+            cstep(c, j, x, y, e);
+            if (j == 0) { // the checkpoint is beta[16 q] before its normalisation
+              qb(v, x, y, false);
+              put_b(nc + q);
+              v = bits(ssub(as_s2(v), s2{as_s2(dppq<0x00>(v)).x, as_s2(dppq<0x00>(v)).x}));
+            } else {
+              qb(v, x, y, (j & 1) == 0);
+            }
           }
         }
       };
-      int q = nc - 1;
-      for (; q - 2 >= 1; q -= 3) {
-        ld_chunk(c2, q - 2, d);
-        bwd_chunk(c0, q);
-        ld_chunk(c0, max(q - 3, 1), d);
-        bwd_chunk(c1, q - 1);
-        ld_chunk(c1, max(q - 4, 1), d);
-        bwd_chunk(c2, q - 2);
+      if (PART) {
+        // the top chunk (its ntop steps) first, then full chunks q, q-1, q-2 in c1, c2, c0 (rotating)
+        ld_chunk(c2, max(nc - 3, 1), d);
+        bwd_chunk(c0, nc - 1, ntop);
+        int q = nc - 2;
+        for (; q - 2 >= 1; q -= 3) {
+          ld_chunk(c0, q - 2, d);
+          bwd_chunk(c1, q, CW);
+          ld_chunk(c1, max(q - 3, 1), d);
+          bwd_chunk(c2, q - 1, CW);
+          ld_chunk(c2, max(q - 4, 1), d);
+          bwd_chunk(c0, q - 2, CW);
+        }
+        if (q >= 1) bwd_chunk(c1, q, CW);
+        if (q - 1 >= 1) bwd_chunk(c2, q - 1, CW);
+      } else {
+        int q = nc - 1;
+        for (; q - 2 >= 1; q -= 3) {
+          ld_chunk(c2, q - 2, d);
+          bwd_chunk(c0, q, CW);
+          ld_chunk(c0, max(q - 3, 1), d);
+          bwd_chunk(c1, q - 1, CW);
+          ld_chunk(c1, max(q - 4, 1), d);
+          bwd_chunk(c2, q - 2, CW);
+        }
+        if (q >= 1) bwd_chunk(c0, q, CW);
+        if (q - 1 >= 1) bwd_chunk(c1, q - 1, CW);
       }
-      if (q >= 1) bwd_chunk(c0, q);
-      if (q - 1 >= 1) bwd_chunk(c1, q - 1);
       if (wave == 1) SP_T(3);
     }
   } else if (B8 && wave == 0) {
@@ -1355,7 +1416,7 @@ __global__ __launch_bounds__(TD_SPREAD_THREADS) void k_win_spread(const TdGroup 
     St8 o;
     st_fill(o, B8 ? 0 : -TD_INF, B8 ? 0 : -TD_INF);
     Chunk<MODE> c0, c1, c2;
-    {
+    if (!PART || (L & 3) == 0) {
       Grp<MODE> pg[10];
       const int gp = (L - TD_OVERLAP) >> 2;
 #pragma unroll
@@ -1369,10 +1430,24 @@ __global__ __launch_bounds__(TD_SPREAD_THREADS) void k_win_spread(const TdGroup 
         astep(o, x, y);
         pnorm(k, o);
       }
+    } else { // element loads, 8 steps at a time (see the 16-bit form)
+      ld_chunk(c0, 0, d);
+      ld_chunk(c1, 1, d);
+      for (int k0 = 0; k0 < TD_OVERLAP; k0 += 8) {
+        s2 xs[8], ys[8];
+#pragma unroll
+        for (int u = 0; u < 8; u++) ld_step(L - TD_OVERLAP + k0 + u, dp, xs[u], ys[u]);
+#pragma unroll
+        for (int u = 0; u < 8; u++) {
+          astep(o, xs[u], ys[u]);
+          pnorm(k0 + u, o);
+        }
+      }
     }
     if (d == 0) st_fill(o, 0, B8 ? 0 : -TD_INF);
     auto fwd_chunk = [&](const Chunk<MODE> &c, int q) {
       ck_put(q, d, o);
+      if (PART && q == nc - 1) return; // the top chunk: only the state entering it is needed
 #pragma unroll
       for (int j = 0; j < CW; j++) {
         s2 x, y, e;
@@ -1423,27 +1498,46 @@ __global__ __launch_bounds__(TD_SPREAD_THREADS) void k_win_spread(const TdGroup 
       if (d == NB - 1) o = t;
     }
     ck_put(2 * nc, d, o); // beta[L]
-    auto bwd_chunk = [&](const Chunk<MODE> &c, int q) { // q >= 1
+    auto bwd_chunk = [&](const Chunk<MODE> &c, int q, int n) { // q >= 1; n steps (wave-uniform)
 #pragma unroll
       for (int j = CW - 1; j >= 0; j--) {
-        s2 x, y, e;
-        cstep(c, j, x, y, e);
-        bstep(o, x, y);
-        if (j == 0) ck_put(nc + q, d, o);
-        nrm_k(o, (j & 1) == 0);
+        if (j < n) {
+          s2 x, y, e;
+          cstep(c, j, x, y, e);
+          bstep(o, x, y);
+          if (j == 0) ck_put(nc + q, d, o);
+          nrm_k(o, (j & 1) == 0);
+        }
       }
     };
-    int q = nc - 1;
-    for (; q - 2 >= 1; q -= 3) {
-      ld_chunk(c2, q - 2, d);
-      bwd_chunk(c0, q);
-      ld_chunk(c0, max(q - 3, 1), d);
-      bwd_chunk(c1, q - 1);
-      ld_chunk(c1, max(q - 4, 1), d);
-      bwd_chunk(c2, q - 2);
+    if (PART) {
+      // the top chunk (its ntop steps) first, then full chunks q, q-1, q-2 in c1, c2, c0 (rotating)
+      ld_chunk(c2, max(nc - 3, 1), d);
+      bwd_chunk(c0, nc - 1, ntop);
+      int q = nc - 2;
+      for (; q - 2 >= 1; q -= 3) {
+        ld_chunk(c0, q - 2, d);
+        bwd_chunk(c1, q, CW);
+        ld_chunk(c1, max(q - 3, 1), d);
+        bwd_chunk(c2, q - 1, CW);
+        ld_chunk(c2, max(q - 4, 1), d);
+        bwd_chunk(c0, q - 2, CW);
+      }
+      if (q >= 1) bwd_chunk(c1, q, CW);
+      if (q - 1 >= 1) bwd_chunk(c2, q - 1, CW);
+    } else {
+      int q = nc - 1;
+      for (; q - 2 >= 1; q -= 3) {
+        ld_chunk(c2, q - 2, d);
+        bwd_chunk(c0, q, CW);
+        ld_chunk(c0, max(q - 3, 1), d);
+        bwd_chunk(c1, q - 1, CW);
+        ld_chunk(c1, max(q - 4, 1), d);
+        bwd_chunk(c2, q - 2, CW);
+      }
+      if (q >= 1) bwd_chunk(c0, q, CW);
+      if (q - 1 >= 1) bwd_chunk(c1, q - 1, CW);
     }
-    if (q >= 1) bwd_chunk(c0, q);
-    if (q - 1 >= 1) bwd_chunk(c1, q - 1);
   }
   // ---- phase B's inputs, loaded before the barrier: waves 4.. (idle in phase A) load theirs while
   // phase A runs. The pair's TD_SPREAD_SPLIT workgroups (on as many CUs) each ran phase A and take
@@ -1452,10 +1546,18 @@ __global__ __launch_bounds__(TD_SPREAD_THREADS) void k_win_spread(const TdGroup 
   const int t = t_lo + tid, q = t / NB, d = t % NB;
   const bool has = t < t_hi;
   Chunk<MODE> c;
+  // steps of the lane's task: ntop in the top chunk; past them nothing is stored and no decision counts
+  const int nl = PART && q == nc - 1 ? ntop : CW;
   if (has) {
-    const uint32_t lo = 16u * NB * 4u * (uint32_t)q; // 4 T4 groups per chunk, 16 B per group and chain
+    // 4 T4 groups per chunk, 16 B per group and chain, clamped into the chain (the top chunk's last ones)
+    const uint32_t lo = 16u * NB * 4u * (uint32_t)q;
 #pragma unroll
-    for (int u = 0; u < 4; u++) ld_grp(c.g[u], u, d, lo);
+    for (int u = 0; u < 4; u++) {
+      if (PART)
+        ld_grp(c.g[u], 0, d, 16u * NB * (uint32_t)min(4 * q + u, G4 - 1));
+      else
+        ld_grp(c.g[u], u, d, lo);
+    }
     const uint32_t vo = 32u * (uint32_t)d + 32u * NB * (uint32_t)q;
     c.t[0] = bld128(R.tb, vo, 0);
     c.t[1] = bld128(R.tb, vo, 16);
@@ -1477,14 +1579,41 @@ __global__ __launch_bounds__(TD_SPREAD_THREADS) void k_win_spread(const TdGroup 
     St8 run, bst[CW];
     ck_get(nc + q + 1, d, run); // beta[16 (q + 1)] before normalisation (beta[L] for the top chunk)
     bst[CW - 1] = run;
-    if (q + 1 < nc) nrm_k(run, true);
+    if (!PART) { // every chunk full
+      if (q + 1 < nc) nrm_k(run, true);
 #pragma unroll
-    for (int j = CW - 2; j >= 0; j--) {
-      s2 x, y, e;
-      cstep(c, j + 1, x, y, e);
-      bstep(run, x, y);
-      bst[j] = run;
-      nrm_k(run, ((j + 1) & 1) == 0);
+      for (int j = CW - 2; j >= 0; j--) {
+        s2 x, y, e;
+        cstep(c, j + 1, x, y, e);
+        bstep(run, x, y);
+        bst[j] = run;
+        nrm_k(run, ((j + 1) & 1) == 0);
+      }
+    } else {
+      // tasks of the top chunk (nl < CW steps down from beta[L], which is never normalised) beside
+      // full ones in one wave: per-lane selects, as win_bidir_body's partial chunk, so every metric
+      // stays in a register whatever nl is. bst[j] for j >= nl - 1 is the top value; the steps that
+      // would use those above nl - 1 store nothing.
+      const St8 top = run;
+      const bool part = q == nc - 1;
+#pragma unroll
+      for (int j = CW - 2; j >= 0; j--) {
+        St8 nx = run; // beta[s0+2+j] once j + 1 <= nl - 1
+        if (B8 || (j & 1) == 0) { // k = s0+2+j even (16-bit) / any (B8), unless it is beta[L]
+          St8 nn = nx;
+          nrm_k(nn, true);
+          const bool is_top = part && j + 1 == nl - 1;
+#pragma unroll
+          for (int i = 0; i < 8; i++) nx.s[i] = is_top ? nx.s[i] : nn.s[i];
+        }
+        s2 x, y, e;
+        cstep(c, j + 1, x, y, e);
+        bstep(nx, x, y);
+        const bool above = j >= nl - 1;
+#pragma unroll
+        for (int i = 0; i < 8; i++) run.s[i] = above ? top.s[i] : nx.s[i];
+        bst[j] = run;
+      }
     }
     // alpha with the LLR (win_bidir_body's `alpha_llr`, n = CW)
     St8 o;
@@ -1527,20 +1656,25 @@ __global__ __launch_bounds__(TD_SPREAD_THREADS) void k_win_spread(const TdGroup 
       } else {
         out = wsub(v, e);
       }
-      bst32(__builtin_bit_cast(uint32_t, out), MODE == 1 ? R.a : R.x2, 4u * (uint32_t)tt);
+      // a step past the lane's chunk (j >= nl) stores nothing: its offset lies beyond the buffer's
+      // 2^31 - 1 records, and the range check drops the store
+      bst32(__builtin_bit_cast(uint32_t, out), MODE == 1 ? R.a : R.x2,
+            !PART || j < nl ? 4u * (uint32_t)tt : 0x80000000u);
       if (DOUT) dacc |= dec_bits(v) << j;
 #pragma unroll
       for (int i = 0; i < 8; i++) o.s[i] = B8 ? bmask(smax(mb[i], nw[i])) : smax(mb[i], nw[i]);
       nrm_fwd(o, q, j);
     }
     if (DOUT) {
+      if (PART) dacc &= (0xffffu >> (CW - nl)) * 0x10001u; // no decision bit of a step past the chunk
       D[d * nc + q] = dacc;
       sdw[d * nc + q] = dacc;
     }
   }
   // ---- the decision bytes of the pair's blocks (k_decide's fixed-iteration output, fused: the drop-in
-  // srslte_tdec_iteration's one launch per call), MSB first (turbodecoder.c:353-360). With L a multiple
-  // of 16 the chain-major index of natural position p after DEC1 is p itself; after DEC2 dmap[p].
+  // srslte_tdec_iteration's one launch per call), MSB first (turbodecoder.c:353-360). Natural
+  // position p = d L + k is bit k % 16 of word d nc + k / 16 after DEC1 (h0_byte; p itself when L is a
+  // multiple of 16), and bit dmap[p] of the words after DEC2.
   if (wave == 0) SP_T(5);
   if (DOUT && outb) {
     if (TD_SPREAD_SPLIT > 1) { // the last of the pair's workgroups to finish writes the bytes
@@ -1556,7 +1690,11 @@ __global__ __launch_bounds__(TD_SPREAD_THREADS) void k_win_spread(const TdGroup 
         sdw[i] = __hip_atomic_load(&D[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     __syncthreads();
-    const int nwd = K / 32; // K is a multiple of 16 NB >= 128: whole 32-bit words
+    // exactly K / 8 bytes per row (the drop-in's completion word follows the row): whole 32-bit
+    // words, then the bytes of a last partial word (K is a multiple of 8, not always of 32)
+    const int nbytes = K / 8, nwd = PART ? (nbytes + 3) / 4 : K / 32;
+    const int gap = PART ? CW * nc - L : 0; // a chain's 16 nc decision bits hold L steps
+    const float invL = 1.0f / (float)L;
     const bool w32 = ((uintptr_t)outb & 3u) == 0 && (out_stride & 3u) == 0;
     for (int i = tid; i < 2 * nwd; i += TD_SPREAD_THREADS) {
       const int h = i >= nwd, w = i - h * nwd, cb = 2 * pair + h;
@@ -1565,24 +1703,30 @@ __global__ __launch_bounds__(TD_SPREAD_THREADS) void k_win_spread(const TdGroup 
 #pragma unroll
       for (int j = 0; j < 4; j++) {
         const int p = 32 * w + 8 * j;
+        if (PART && p >= K) break;
         uint32_t v = 0;
         if (MODE != 1) {
-          v = (sdw[p >> 4] >> (16 * h + (p & 15))) & 0xffu;
-        } else {
+          if (!PART) // the chain-major index of p is p itself
+            v = __builtin_bitreverse32((sdw[p >> 4] >> (16 * h + (p & 15))) & 0xffu) >> 24;
+          else
+            v = h0_byte(sdw, NB * nc, L, gap, invL, h, p);
+        } else { // dmap[p]: the bit's index in the decision words (the gap included)
 #pragma unroll
           for (int b = 0; b < 8; b++) {
             const int c = sdm[p + b];
             v |= ((sdw[c >> 4] >> ((c & 15) + 16 * h)) & 1u) << b;
           }
+          v = __builtin_bitreverse32(v) >> 24;
         }
-        word |= (__builtin_bitreverse32(v) >> 24) << (8 * j);
+        word |= v << (8 * j);
       }
       uint8_t *row = outb + (size_t)(G.cb0 + cb) * out_stride;
-      if (w32) {
+      if (w32 && (!PART || 4 * w + 4 <= nbytes)) {
         reinterpret_cast<uint32_t *>(row)[w] = word;
       } else {
 #pragma unroll
-        for (int j = 0; j < 4; j++) row[4 * w + j] = (uint8_t)(word >> (8 * j));
+        for (int j = 0; j < 4; j++)
+          if (!PART || 4 * w + j < nbytes) row[4 * w + j] = (uint8_t)(word >> (8 * j));
       }
     }
     if (flag) { // host-mapped completion word: the caller polls it instead of synchronising the stream
@@ -3408,17 +3552,21 @@ hipError_t halfits_es_part(const TdGroup *dg, int ng, int nblocks, size_t lds, c
 
 // k_win_spread launchers, one per windowed kind (in the part that holds the kind)
 template <int KIND>
-hipError_t spread_part(int mode, const TdGroup *dg, int npairs, size_t lds, bool dec, const TdArrays &a,
+hipError_t spread_part(int mode, bool part, const TdGroup *dg, int npairs, size_t lds, bool dec, const TdArrays &a,
                        const uint8_t *pair_done, uint8_t *outb, size_t out_stride, const SpreadOut &so,
                        hipStream_t st);
-#define SPREAD1(nb, div, m, dout, b8)                                                              \
-  hipLaunchKernelGGL((k_win_spread<nb, div, m, dout, b8>), dim3(npairs * TD_SPREAD_SPLIT),           \
+#define SPREAD2(nb, div, m, dout, b8, pt)                                                          \
+  hipLaunchKernelGGL((k_win_spread<nb, div, m, dout, b8, pt>), dim3(npairs * TD_SPREAD_SPLIT),       \
                      dim3(TD_SPREAD_THREADS), lds, st, dg, (const s4 *)a.SP0, (s2 *)a.XP1, (s2 *)a.A, \
                      (uint32_t *)a.D, (const s2 *)a.T, a.plane, pair_done, outb, out_stride, so.cnt, \
                      so.flag, so.seq)
+#define SPREAD1(nb, div, m, dout, b8)                                                              \
+  do {                                                                                             \
+    if (part) SPREAD2(nb, div, m, dout, b8, true); else SPREAD2(nb, div, m, dout, b8, false);      \
+  } while (0)
 #define SPREAD(KIND, nb, div, b8)                                                                  \
   template <>                                                                                      \
-  hipError_t spread_part<KIND>(int mode, const TdGroup *dg, int npairs, size_t lds, bool dec,      \
+  hipError_t spread_part<KIND>(int mode, bool part, const TdGroup *dg, int npairs, size_t lds, bool dec, \
                                const TdArrays &a, const uint8_t *pair_done, uint8_t *outb,         \
                                size_t out_stride, const SpreadOut &so, hipStream_t st) {          \
     if (mode == 1) {                                                                               \
@@ -3441,6 +3589,7 @@ SPREAD(TD_KIND_B32, 32, 1, true)
 #endif
 #undef SPREAD
 #undef SPREAD1
+#undef SPREAD2
 
 #define NO_ES (void)dg; (void)ng; (void)nblocks; (void)lds; (void)a; (void)es; (void)st; return hipErrorInvalidValue
 #if TD_PART == 1
@@ -3491,25 +3640,30 @@ int spread_max_pairs() { return TD_SPREAD_MAX_PAIRS; }
 
 bool spread_ok(int kind, int K, int nb) {
   const bool win = kind == TD_KIND_W16 || kind == TD_KIND_W8 || kind == TD_KIND_B16 || kind == TD_KIND_B32;
-  return win && nb > 1 && K % nb == 0 && (K / nb) % TD_BIDIR_CW == 0 && K / nb >= 48;
+  return win && nb > 1 && K % nb == 0 && K / nb > TD_OVERLAP; // the engine's own rule (check_spec)
 }
 
 hipError_t launch_halfit_spread(int n, int kind, const TdGroup *dg, int npairs, int K, int nb, bool dec,
                                 const TdArrays &arr, const uint8_t *pair_done, hipStream_t st,
                                 uint8_t *outb, size_t out_stride, const SpreadOut &so) {
   if (npairs <= 0) return hipSuccess;
-  if (!spread_ok(kind, K, nb) || npairs > TD_SPREAD_MAX_PAIRS || K > 6144 ||
-      K / TD_BIDIR_CW > TD_SPREAD_THREADS * TD_SPREAD_SPLIT || (outb && (!dec || !so.cnt)))
+  if (!spread_ok(kind, K, nb) || npairs > TD_SPREAD_MAX_PAIRS || K > 6144) return hipErrorInvalidValue;
+  const int nc = (K / nb + TD_BIDIR_CW - 1) / TD_BIDIR_CW; // chunks per chain, the last one possibly partial
+  // one phase-B task per thread; the decision words of a pair fit the kernel's staging array; the
+  // completion word is stored by the one workgroup of a one-pair launch
+  if (nb * nc > TD_SPREAD_THREADS * TD_SPREAD_SPLIT || nb * nc > 6144 / 16 || (outb && (!dec || !so.cnt)) ||
+      (so.flag && npairs > 1))
     return hipErrorInvalidValue;
   const int mode = (n & 1) ? 1 : (n == 0 ? 2 : 0);
   TdArrays a = arr;
   if (!dec) a.D = nullptr;
-  const size_t lds = (size_t)(2 * (K / nb / TD_BIDIR_CW) + 1) * nb * 32;
+  const size_t lds = (size_t)(2 * nc + 1) * nb * 32;
+  const bool part = (K / nb) % TD_BIDIR_CW != 0; // a partial last chunk: the kernel's PART form
   switch (kind) {
-  case TD_KIND_W16: return spread_part<TD_KIND_W16>(mode, dg, npairs, lds, dec, a, pair_done, outb, out_stride, so, st);
-  case TD_KIND_W8: return spread_part<TD_KIND_W8>(mode, dg, npairs, lds, dec, a, pair_done, outb, out_stride, so, st);
-  case TD_KIND_B16: return spread_part<TD_KIND_B16>(mode, dg, npairs, lds, dec, a, pair_done, outb, out_stride, so, st);
-  case TD_KIND_B32: return spread_part<TD_KIND_B32>(mode, dg, npairs, lds, dec, a, pair_done, outb, out_stride, so, st);
+  case TD_KIND_W16: return spread_part<TD_KIND_W16>(mode, part, dg, npairs, lds, dec, a, pair_done, outb, out_stride, so, st);
+  case TD_KIND_W8: return spread_part<TD_KIND_W8>(mode, part, dg, npairs, lds, dec, a, pair_done, outb, out_stride, so, st);
+  case TD_KIND_B16: return spread_part<TD_KIND_B16>(mode, part, dg, npairs, lds, dec, a, pair_done, outb, out_stride, so, st);
+  case TD_KIND_B32: return spread_part<TD_KIND_B32>(mode, part, dg, npairs, lds, dec, a, pair_done, outb, out_stride, so, st);
   default: return hipErrorInvalidValue;
   }
 }

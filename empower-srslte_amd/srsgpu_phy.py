@@ -315,6 +315,7 @@ _sig = {
     "srsgpu_tdec_batch_decode": (_i32, [_vp, _i32, _i32, ctypes.POINTER(_vp), _u32, _u32, _u32,
                                         _u32, _u32, ctypes.POINTER(_vp), _u8p, _u32p]),
     "srsgpu_tdec_input_len": (_u32, [_i32, _i32, _u32]),
+    "srsgpu_tdec_latency_form": (_i32, [_i32, _u32]),
     "srsgpu_tdec_batch_read_state": (_i32, [_vp, _u32, _i16p, _i16p]),
     "srsgpu_dlsch_create": (_i32, [ctypes.POINTER(_vp), _u32, _u32, _u32]),
     "srsgpu_dlsch_destroy": (None, [_vp]),
@@ -471,6 +472,12 @@ def _u8(a):
 
 def input_len(impl, sb_layout, K):
     return _lib.srsgpu_tdec_input_len(impl, sb_layout, K)
+
+
+def latency_form(impl, K):
+    """srsgpu_tdec_latency_form: 1 when a job of a few pairs of (impl, K) runs on k_win_spread, 0 when it
+    takes the throughput kernels, -1 for an invalid impl or K (host code only)"""
+    return _lib.srsgpu_tdec_latency_form(impl, K)
 
 
 def autoimp_get_subblocks(K):

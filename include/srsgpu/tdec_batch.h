@@ -83,6 +83,13 @@ int srsgpu_tdec_batch_read_state(srsgpu_tdec_batch_t *q, uint32_t cb, int16_t *a
 /* Input length (int16 elements) one CB needs for (impl, sb_layout, K). */
 uint32_t srsgpu_tdec_input_len(int impl, int sb_layout, uint32_t long_cb);
 
+/* Which kernels a small job takes: 1 when a job of at most 16 pairs (32 code blocks) of one size
+ * long_cb decoded by `impl` runs on the latency kernel (k_win_spread, one workgroup per pair: the
+ * form srslte_tdec_iteration needs) — every size a windowed decoder takes, unless SRSGPU_SPREAD=0;
+ * 0 when it takes the throughput kernels (the SSE and generic decoders); -1 for an invalid long_cb
+ * or impl, or a size the chosen window decoder refuses. Host code only: no GPU call. */
+int srsgpu_tdec_latency_form(int impl, uint32_t long_cb);
+
 /* Decoder launch schedule (process-wide; results are identical under every setting):
  *   fused      1: fixed-iteration jobs run all half-iterations in one launch per decoder kind;
  *              0: one launch per half-iteration (SRSGPU_TDEC_FUSED)
